@@ -21,12 +21,21 @@ starts N child processes itself (one per GPU, ``RANK`` / ``LOCAL_RANK`` / ``WORL
 ``torch.distributed.run`` it runs as the given rank. A world size different from ``--gpus`` is an
 error. Only the timing barriers and the max-over-ranks reduction are collectives.
 
+A plain run (``python bench.py --gpus N --steps K --warmup W``) does what the headline figure
+needs and no more: it builds config B, decodes and verifies it once, warms up, times the K steps
+(in three blocks), verifies the last step's outputs and prints the line. ``--dump-outputs DIR``
+also writes those outputs (or a fixed sample of the large ones) as ``DIR/<name>.npy``
+(:func:`dump_outputs`); the workloads are seeded, so two builds run with the same arguments
+decode the same inputs. ``--full`` adds everything else: config C, the same-run copy ceiling, the
+fresh-batch steps, the committed PMC traffic and the CPU baselines.
+
 Rank 0 prints ONE JSON line with the metric, a ``roofline`` object per config (algorithmic bytes
 R+W per launch / HIP-event kernel time on the launch stream, vs the 8 TB/s HBM3E peak and the
-6.29 TB/s float4 copy the microarchitecture guide records; ``traffic`` from a committed
-rocprofv3 PMC summary of the SAME workload and kernel, else null) and a ``cpu_baseline`` object
-per config: the reference reader restated with its per-call coder construction
-(``oracle/mds_oracle.py``, kind "port") timed on host cores, 1 core and all cores of the box's share.
+6.29 TB/s float4 copy the microarchitecture guide records; with ``--full``, ``traffic`` from a
+committed rocprofv3 PMC summary of the SAME workload and kernel, else null) and, with ``--full``,
+a ``cpu_baseline`` object per config: the reference reader restated with its per-call coder
+construction (``oracle/mds_oracle.py``, kind "port") timed on host cores, 1 core and all cores of
+the box's share.
 """
 
 from __future__ import annotations
@@ -61,12 +70,20 @@ def parse_args(argv=None):
     # untimed steps first: the decode reaches its steady rate after ~20 launches (config C 2 %
     # faster after 30 warm-up steps than after 3, profiles/r02/warmup.txt)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--config', choices=['B', 'C', 'BC'], default='BC',
-                    help='B = headline line only; BC = B plus the config_c object')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline figure too: the config_c object, the '
+                    'same-run copy ceiling, the fresh-batch steps, the committed PMC traffic and '
+                    'the CPU baselines (a plain run times config B and prints its line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one decoded as DIR/<name>.npy '
+                    '(float32 / float64, at most 64 MB in all: see dump_outputs)')
+    ap.add_argument('--config', choices=['B', 'C', 'BC'], default=None,
+                    help='B = headline line only; BC = B plus the config_c object (default: BC '
+                    'with --full, else B)')
     ap.add_argument('--shards', type=int, default=0,
                     help='shards per GPU (0: 62 for B, 64 for C = ~1M samples)')
     ap.add_argument('--cpu-seconds', type=float, default=2.0,
-                    help='CPU baseline seconds per leg (0 disables)')
+                    help='--full: CPU baseline seconds per leg (0 disables)')
     ap.add_argument('--cpu-procs', type=int, default=0,
                     help='all-core CPU leg processes (0: the box share, see cpu_cores())')
     ap.add_argument('--single', action='store_true',
@@ -78,20 +95,30 @@ def parse_args(argv=None):
                     '§9: the decode holds the CUs, so the scan competes instead of overlapping)')
     ap.add_argument('--no-verify', action='store_true')
     ap.add_argument('--no-copy-probe', dest='copy_probe', action='store_false',
-                    help='skip the same-run copy-ceiling measurement')
+                    help='--full: skip the same-run copy-ceiling measurement')
     ap.add_argument('--dist', action='store_true',
                     help='set up the process group even for one rank (nccl = RCCL on the GPU): '
                          'runs the barrier / max-over-ranks / gather collectives of the N > 1 '
                          'path on a one-GPU box')
     ap.add_argument('--fresh-steps', type=int, default=6,
-                    help='ragged configs: also time this many steps over two distinct resident '
-                    'batches taken in turn, each with a decoder of its own (its sizing included: '
-                    'the totals read back and the outputs allocated; and the single-pass form, '
-                    'outputs at their upper bound); 0 disables')
+                    help='--full, ragged configs: also time this many steps over two distinct '
+                    'resident batches taken in turn, each with a decoder of its own (its sizing '
+                    'included: the totals read back and the outputs allocated; and the single-pass '
+                    'form, outputs at their upper bound); 0 disables')
     ap.add_argument('--dry-run', action='store_true',
                     help='no GPU: exercise the launcher, process group (gloo) and shard '
                     'ownership only (CPU test hook)')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: the headline's steps only
+        args.copy_probe = False
+        args.cpu_seconds = 0.0
+        args.fresh_steps = 0
+    return args
+
+
+def configs_of(args):
+    config = args.config or ('BC' if args.full else 'B')
+    return ['B', 'C'] if config == 'BC' else [config]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -368,6 +395,61 @@ def copy_ceiling(batch, iters=10, dst=None):
             'bytes_per_launch': 2 * src.numel()}
 
 
+# ---------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step decoded, as .npy files two builds can be compared by
+DUMP_BUDGET = 56 << 20  # bytes of array data over the whole run (64 MB less headers and slack)
+DUMP_SEED = 20240  # of the row samples: the same rows in every run of the same arguments
+DUMP_CHUNK = 4096  # a sampled "row" of a 1-D array (ragged values, offsets): this many elements
+
+
+def _exact_float(t):
+    """``t`` as float32 / float64 without loss. Integers keep their values; 64-bit ones become a
+    last axis of 2, (signed high half, unsigned low half). Floating-point columns are written as
+    their BIT PATTERNS, taken as signed integers of their width: config B's ``x`` holds every
+    float32 bit pattern, NaNs of every payload among them, the decode is checked bit for bit, and
+    no file holds a NaN that a comparison would have to special-case."""
+    if t.dtype == torch.bool:
+        return t.to(torch.float32)
+    size = t.element_size()
+    if t.is_floating_point() or t.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32,
+                                                torch.int64):
+        t = t.view({1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[size])
+    if size == 8:
+        return torch.stack([t >> 32, t & 0xffffffff], dim=-1).to(torch.float64)
+    return t.to(torch.float32 if size <= 2 else torch.float64)
+
+
+def dump_outputs(out_dir, prefix, decoded, budget):
+    """Write the columns of ``decoded`` (a DecodedBatch) as ``out_dir/<prefix><column>.npy``, a
+    ragged column as ``..._values``, ``..._offsets`` and (str) ``..._flags``, each converted by
+    :func:`_exact_float`. The arrays share ``budget`` bytes equally; one that needs more is
+    written as a seeded sample of its rows (1-D arrays: of its DUMP_CHUNK-element chunks, a last
+    partial chunk left out), in ascending order, with the rows' indices in ``<name>.rows.npy``."""
+    from streaming_amd.decoder import RaggedColumn
+    arrays = {}
+    for name, col in decoded.columns.items():
+        if isinstance(col, RaggedColumn):
+            arrays[f'{name}_values'], arrays[f'{name}_offsets'] = col.values, col.offsets
+            if col.flags is not None:
+                arrays[f'{name}_flags'] = col.flags
+        else:
+            arrays[name] = col
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(len(arrays), 1)
+    rng = np.random.default_rng(DUMP_SEED)
+    for name, t in arrays.items():
+        wide = 16 if t.element_size() == 8 else 8 if t.element_size() > 2 else 4
+        if t.numel() * wide > share:
+            if t.dim() == 1:
+                t = t[:t.numel() // DUMP_CHUNK * DUMP_CHUNK].view(-1, DUMP_CHUNK)
+            t = t.reshape(t.shape[0], -1)
+            k = max(1, share // (t.shape[1] * wide + 8))
+            rows = np.sort(rng.choice(t.shape[0], size=min(k, t.shape[0]), replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+            np.save(os.path.join(out_dir, f'{prefix}{name}.rows.npy'), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, f'{prefix}{name}.npy'), _exact_float(t).cpu().numpy())
+
+
 BLOCKS = 3  # the K timed steps of each config, split into blocks interleaved across configs
 
 
@@ -547,8 +629,12 @@ def finish(args, leg, world, rank, tmpdir):
     copy = None
     if copies:  # the block whose copy ceiling is the median one, with every shape's rate
         copy = sorted(copies, key=lambda c: c['GBps'])[len(copies) // 2]
+    if args.dump_outputs:
+        prefix = f'{config}_' if world == 1 else f'rank{rank}_{config}_'
+        dump_outputs(args.dump_outputs, prefix, leg.dec.result(),
+                     DUMP_BUDGET // (world * len(configs_of(args))))
     key = workload_key(config, batch, W)
-    traffic, traffic_src = committed_traffic(key, leg.kernel)
+    traffic, traffic_src = committed_traffic(key, leg.kernel) if args.full else (None, None)
     spb = [b['ms_per_step'] for b in leg.blocks]
     blocks = [{k: v for k, v in b.items() if not k.startswith('_')} for b in leg.blocks]
     result = {
@@ -681,7 +767,8 @@ def measure_all(args, configs, world, rank, dev, tmpdir):
 def dry_run(args, world, rank):
     """No GPU: the launcher's ranks, their process group and shard ownership (CPU test hook)."""
     lines = {}
-    for config in ('B', 'C') if args.config == 'BC' else (args.config, ):
+    # (no config named: every config of the benchmark, as --full runs them)
+    for config in configs_of(args) if args.config else ('B', 'C'):
         mine, total = shard_plan(args, config, rank, world)
         lines[config] = gather_objects(world, {'rank': rank, 'shards': mine, 'total': total})
     # the N-GPU line's per-rank report, from made-up timings (rank r: 1 + r/10 ms per step)
@@ -703,13 +790,15 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return launch(args, argv)  # before any GPU call in this process
     world, rank, local, dev = init_dist(args)
     if args.dry_run:
         dry_run(args, world, rank)
         return 0
-    configs = ['B', 'C'] if args.config == 'BC' else [args.config]
+    configs = configs_of(args)
     with tempfile.TemporaryDirectory(prefix='mdsx_cpu_') as tmpdir:
         results = measure_all(args, configs, world, rank, dev, tmpdir)
     head = results[configs[0]]
@@ -722,6 +811,7 @@ def main(argv=None):
             'n_gpus': world,
             'steps': args.steps,
             'warmup': args.warmup,
+            'full': args.full,
             'ms_per_step': head['ms_per_step'],
             'higher_is_better': True,
             'scaling': 'weak',

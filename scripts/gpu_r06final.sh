@@ -16,7 +16,7 @@ cat "$OUT/smoke.log"
 fi
 [ "$PART" = tests ] && exit 0
 for i in 1 2; do
-  timeout -k 10 600 python3 bench.py > "$OUT/bench$i.json" 2> "$OUT/bench$i.err" || { tail -30 "$OUT/bench$i.err"; exit 1; }
+  timeout -k 10 600 python3 bench.py --full > "$OUT/bench$i.json" 2> "$OUT/bench$i.err" || { tail -30 "$OUT/bench$i.err"; exit 1; }
   python3 - "$OUT/bench$i.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

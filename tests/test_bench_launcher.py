@@ -90,6 +90,67 @@ def test_committed_traffic_is_keyed_on_workload_kernel_and_sources(tmp_path, mon
     assert bench.committed_traffic('B:k', 'decode_kernel<4, true>') == (None, None)
 
 
+def test_plain_run_is_the_headline_only():
+    """Without --full the benchmark times config B and nothing else; --full keeps every leg."""
+    import bench
+    plain = bench.parse_args(['--gpus', '1', '--steps', '5', '--warmup', '2'])
+    assert bench.configs_of(plain) == ['B']
+    assert (plain.steps, plain.warmup) == (5, 2)
+    assert not plain.copy_probe and plain.cpu_seconds == 0 and plain.fresh_steps == 0
+    assert plain.dump_outputs is None
+    full = bench.parse_args(['--full'])
+    assert bench.configs_of(full) == ['B', 'C']
+    assert full.copy_probe and full.cpu_seconds > 0 and full.fresh_steps > 0
+    assert bench.configs_of(bench.parse_args(['--full', '--config', 'C'])) == ['C']
+    assert bench.configs_of(bench.parse_args(['--config', 'BC'])) == ['B', 'C']
+
+
+def test_dump_outputs_is_exact_seeded_and_bounded(tmp_path):
+    """--dump-outputs: float32 / float64 files that lose nothing (floats as bit patterns, 64-bit
+    integers as halves), large arrays as the same seeded rows every time, within the budget."""
+    import numpy as np
+    import torch
+
+    import bench
+    from streaming_amd.decoder import DecodedBatch, RaggedColumn
+    g = torch.Generator().manual_seed(3)
+    n = 1000
+    x = torch.randint(0, 256, (n, 64), dtype=torch.uint8, generator=g).view(torch.float32)
+    x[0, 0] = float('nan')
+    big = torch.randint(-2**62, 2**62, (n, ), dtype=torch.int64, generator=g)
+    ids = torch.arange(n, dtype=torch.int32) - 5
+    lens = torch.randint(0, 40, (n, ), generator=g)
+    offs = torch.zeros(n + 1, dtype=torch.int64)
+    offs[1:] = lens.cumsum(0)
+    vals = torch.randint(0, 256, (int(offs[-1]), ), dtype=torch.uint8, generator=g)
+    flags = torch.zeros(n, dtype=torch.uint8)
+    dec = DecodedBatch({'id': ids, 'x': x, 'n': big, 's': RaggedColumn(vals, offs, flags)}, n)
+    budget = 6 * 16384  # x (16 values a row, 8 bytes each) and values do not fit their sixth
+    a, b = tmp_path / 'a', tmp_path / 'b'
+    bench.dump_outputs(str(a), 'T_', dec, budget)
+    bench.dump_outputs(str(b), 'T_', dec, budget)
+    names = sorted(p.name for p in a.iterdir())
+    assert names == sorted(p.name for p in b.iterdir())
+    assert names == ['T_id.npy', 'T_n.npy', 'T_s_flags.npy', 'T_s_offsets.npy', 'T_s_values.npy',
+                     'T_s_values.rows.npy', 'T_x.npy', 'T_x.rows.npy']
+    got = {p.name[2:-4]: np.load(p) for p in a.iterdir()}
+    assert sum(v.nbytes for v in got.values()) <= budget
+    for name, v in got.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), name
+        assert np.array_equal(v, np.load(b / f'T_{name}.npy')), name
+    assert np.array_equal(got['id'], ids.numpy().astype(np.float64))
+    halves = got['n'].astype(np.int64)
+    assert np.array_equal((halves[:, 0] << 32) | halves[:, 1], big.numpy())
+    rows = got['x.rows'].astype(np.int64)
+    assert 1 < len(rows) < n and (np.diff(rows) > 0).all()
+    assert np.array_equal(got['x'].astype(np.int32), x.view(torch.int32).numpy()[rows])
+    chunks = got['s_values.rows'].astype(np.int64)
+    want = vals[:vals.numel() // bench.DUMP_CHUNK * bench.DUMP_CHUNK].view(-1, bench.DUMP_CHUNK)
+    assert np.array_equal(got['s_values'], want.numpy()[chunks].astype(np.float32))
+    assert np.array_equal(got['s_offsets'].astype(np.int64)[:, 0], np.zeros(n + 1, np.int64))
+    assert np.array_equal(got['s_offsets'].astype(np.int64)[:, 1], offs.numpy())
+
+
 def test_block_sizes():
     """bench.py splits each config's K timed steps into interleaved blocks."""
     import bench
