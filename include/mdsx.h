@@ -214,6 +214,53 @@ int mdsx_decode_shards_single(const mdsx_plan* plan, const mdsx_batch* batch,
 int mdsx_decode_sample(const mdsx_plan* plan, const uint8_t* d_data, uint32_t n, uint8_t* d_values,
                        int64_t* d_meta, void* stream);
 
+/* Many samples, each sliced exactly as mdsx_decode_sample slices one, straight into device batch
+ * columns, in two launches with no per-sample sync: the device batch path's patch for the samples
+ * the whole-shard decodes refuse (order.DeviceSampleGather, malformed='reference').
+ *   d_data           : device buffer of data_bytes bytes holding the m samples' bytes (each what
+ *                      get_sample_data returned), anywhere and at any alignment -- back to back
+ *                      is fine -- with at least 64 readable bytes of the buffer before the first
+ *                      sample and after the last (the aligned loads of the copy reach that far
+ *                      past a sample; a sample whose span does not leave that slack inside
+ *                      [0, data_bytes) is not read: its status is MDSX_E_BOUNDS)
+ *   d_sample_offsets : device uint64[m], each sample's first byte in d_data
+ *   d_sample_bytes   : device uint32[m], each sample's length (0 is legal)
+ * Per sample, a status and the column it names (-1: none): */
+#define MDSX_SAMPLE_OK 0          /* every column got its whole slice (bytes after the last column
+                                     are allowed)                                                */
+#define MDSX_SAMPLE_CLIPPED 1     /* every size head is present and every fixed column whole, but a
+                                     ragged column's slice is shorter than its head says (the
+                                     first such column): the reference returns the short bytes,
+                                     or raises UnicodeDecodeError where a str is cut in a sequence */
+#define MDSX_SAMPLE_SHORT_HEAD 2  /* a u32 size head is cut short (the first in column order):
+                                     numpy raises ValueError there; every ragged length is 0      */
+#define MDSX_SAMPLE_SHORT_FIXED 3 /* a fixed column's slice is shorter than its row (the first
+                                     such column): the reference's numpy decode raises for every
+                                     fixed encoding, empty or short                               */
+/* Pass 1 (sizes).
+ *   d_lengths : device int64[num_var][m + 1]: the clipped length of sample k's slice of the v-th
+ *               variable column goes to d_lengths[v][k + 1]; d_lengths[v][0] is not written, so
+ *               with it zeroed an inclusive prefix sum over each row gives that column's
+ *               offsets[m + 1] (the caller's; its last entry sizes the column's values)
+ *   d_status  : device int32[m][2]: status, column
+ * Column starts are summed in 64 bits and clipped to the sample (the reference, under NumPy 2,
+ * wraps its running offset at 2^32: the one known difference, as for mdsx_decode_sample). */
+int mdsx_decode_samples_sizes(const mdsx_plan* plan, const uint8_t* d_data, uint64_t data_bytes,
+                              const uint64_t* d_sample_offsets, const uint32_t* d_sample_bytes,
+                              uint64_t m, int64_t* d_lengths, int32_t* d_status, void* stream);
+/* Pass 2 (copy), same samples.
+ *   outs : HOST array of plan->ncols column outputs (device pointers inside). Ragged columns:
+ *          .data the values (.capacity bytes), .offsets int64[m + 1] from pass 1's lengths,
+ *          .flags (str; may be NULL) uint8[m], set to 1 where the slice AS CLIPPED is not
+ *          well-formed UTF-8, else 0. Fixed columns: .data [m][row_bytes], zeroed by the caller;
+ *          row k is written when every fixed column of sample k is whole (status 0 or 1) and is
+ *          left alone otherwise.
+ * Sample k's slice of a ragged column is written to [offsets[k], offsets[k + 1]) of its values
+ * and no byte outside that range is touched (nor any byte at all if the range leaves .capacity). */
+int mdsx_decode_samples_copy(const mdsx_plan* plan, const uint8_t* d_data, uint64_t data_bytes,
+                             const uint64_t* d_sample_offsets, const uint32_t* d_sample_bytes,
+                             uint64_t m, const mdsx_column_out* outs, void* stream);
+
 /* ---- batch gather by sample id ---------------------------------------------
  * out[k] = column[idx[k]] over already-decoded columns: the device side of the reference's
  * per-sample iteration over a worker's sample ids (StreamingDataset.__iter__ ->

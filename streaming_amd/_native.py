@@ -40,6 +40,12 @@ KIND_NDARRAY = 3
 
 MAX_COLUMNS = 64
 BATCH_PAD = 256
+SAMPLE_SLACK = 64  # readable bytes before and after the samples of mdsx_decode_sample(s)
+# mdsx_decode_samples_* per-sample status (MDSX_SAMPLE_*)
+SAMPLE_OK = 0
+SAMPLE_CLIPPED = 1
+SAMPLE_SHORT_HEAD = 2
+SAMPLE_SHORT_FIXED = 3
 GATHER_SRC_SHIFT = 40  # MDSX_GATHER_SRC_SHIFT: multi-source gather ids are source << 40 | row
 
 # Every function include/mdsx.h declares (checked by tests/test_native_abi.py).
@@ -60,6 +66,8 @@ EXPORTED_SYMBOLS = (
     'mdsx_decode_shards',
     'mdsx_decode_shards_single',
     'mdsx_decode_sample',
+    'mdsx_decode_samples_sizes',
+    'mdsx_decode_samples_copy',
     'mdsx_copy_probe',
     'mdsx_copy_probe_variant',
     'mdsx_copy_to_host',
@@ -182,6 +190,12 @@ def _declare(handle: ctypes.CDLL) -> None:
     ]
     handle.mdsx_decode_sample.restype = c_int
     handle.mdsx_decode_sample.argtypes = [vp, vp, c_u32, vp, vp, vp]
+    handle.mdsx_decode_samples_sizes.restype = c_int
+    handle.mdsx_decode_samples_sizes.argtypes = [vp, vp, c_u64, vp, vp, c_u64, vp, vp, vp]
+    handle.mdsx_decode_samples_copy.restype = c_int
+    handle.mdsx_decode_samples_copy.argtypes = [
+        vp, vp, c_u64, vp, vp, c_u64, ctypes.POINTER(ColumnOut), vp
+    ]
     handle.mdsx_copy_probe.restype = c_int
     handle.mdsx_copy_probe.argtypes = [vp, vp, c_u64, vp]
     handle.mdsx_copy_probe_variant.restype = c_int

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(HERE)
 SOURCES = [
     os.path.join(HERE, 'csrc', name)
     for name in ('mdsx_kernels.hip', 'mdsx_stage.hip', 'mdsx_run.hip', 'mdsx_rows.hip', 'mdsx_swave.hip',
-                 'mdsx_sample.hip', 'mdsx_encode.hip', 'mdsx_hash.hip', 'mdsx_plan.cpp')
+                 'mdsx_sample.hip', 'mdsx_samples.hip', 'mdsx_encode.hip', 'mdsx_hash.hip', 'mdsx_plan.cpp')
 ]
 HEADERS = [os.path.join(HERE, 'csrc', name)
            for name in ('mdsx_internal.h', 'mdsx_device.h', 'mdsx_decode.h', 'mdsx_ring.h',
@@ -86,6 +86,8 @@ ISA_CHECKED = {
     'mdsx_rows.hip': ('rows_decode_kernel',),
     'mdsx_kernels.hip': ('rowwave_decode_kernel',),
     'mdsx_swave.hip': ('swave_decode_kernel',),
+    # the batched sample decode: a wave picks its sample, then copies with readlane / DPP
+    'mdsx_samples.hip': ('samples_sizes_kernel', 'samples_copy_kernel'),
 }
 
 

@@ -77,14 +77,18 @@ class LocalDataset(Array, Dataset):
         return self.shards[shard_id][index_in_shard]
 
     def iter_batches(self, sample_ids: Union[Sequence[int], np.ndarray, torch.Tensor],
-                     batch_size: int) -> Iterator[DecodedBatch]:
+                     batch_size: int, malformed: str = 'strict') -> Iterator[DecodedBatch]:
         """Device batches of ``batch_size`` samples in the order of ``sample_ids`` (global ids,
         ``-1`` padding skipped as the reference's ``_each_sample_id`` does,
         ``dataset.py:1430-1473``; e.g. one worker's slice of ``generate_work``'s ids,
         :func:`streaming_amd.order.worker_sample_ids`): the shards a batch touches are decoded on
         demand through the bounded decoded-shard cache and each batch is gathered on the device
-        (:class:`streaming_amd.order.DeviceSampleGather`)."""
-        return self.sample_gather.iter_batches(sample_ids, batch_size)
+        (:class:`streaming_amd.order.DeviceSampleGather`). ``malformed``: ``'strict'`` -- a
+        batch reading a sample that breaks the MDS layout raises -- or ``'reference'`` -- it
+        yields the clipped values the reference's loader yields and raises only where the
+        reference raises."""
+        return DeviceSampleGather(self.shards, malformed=malformed).iter_batches(sample_ids,
+                                                                                batch_size)
 
     @property
     def sample_gather(self) -> DeviceSampleGather:

@@ -22,7 +22,8 @@ Errors follow ``get_item``: a missing shard file raises ``FileNotFoundError`` (t
 re-prepares it, ``dataset.py:1274-1291``); a malformed sample raises for that sample only
 (``IndexError`` for an empty one, ``ValueError`` for a range error); ``str`` values that are not
 well-formed UTF-8 come back flagged in the column's ``flags`` (where ``bytes.decode('utf-8')``
-raises, ``encodings.py:80-81``).
+raises, ``encodings.py:80-81``). With ``malformed='reference'`` a malformed sample is served as
+the reference serves it instead -- clipped -- and the batch raises only where the reference does.
 """
 
 from __future__ import annotations
@@ -33,7 +34,8 @@ from typing import Iterator, Sequence, Union
 import numpy as np
 import torch
 
-from streaming_amd.decoder import DecodedBatch, RaggedColumn, gather_sources
+from streaming_amd import _native
+from streaming_amd.decoder import DecodedBatch, RaggedColumn, _status_error, gather_sources
 from streaming_amd.reader import MDSReader
 
 __all__ = ['worker_sample_ids', 'loader_batches', 'concat_batches', 'DeviceSampleGather']
@@ -104,9 +106,19 @@ class DeviceSampleGather:
     Args:
         shards: the dataset's readers (``LocalDataset.shards``, or the readers a device
             ``Stream`` returns).
+        malformed: what a batch does with a sample that breaks the MDS layout (a size head past
+            its sample, a sample cut short, offsets past the file, ``end < begin``).
+            ``'strict'`` (default): the batch raises -- the reference's own exception where the
+            reference raises for that sample, else ``ValueError`` -- and a shard whose header does
+            not match its file serves no batch. ``'reference'``: the batch yields what the
+            reference's loader yields, sample by sample -- the clipped values -- and raises only
+            where the reference raises (:meth:`_gather_reference`).
     """
 
-    def __init__(self, shards: Sequence[MDSReader]) -> None:
+    def __init__(self, shards: Sequence[MDSReader], malformed: str = 'strict') -> None:
+        if malformed not in ('strict', 'reference'):
+            raise ValueError(f"malformed must be 'strict' or 'reference', got {malformed!r}")
+        self.malformed = malformed
         self.shards = list(shards)
         counts = np.array([s.samples for s in self.shards], np.int64)
         self.starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
@@ -136,6 +148,8 @@ class DeviceSampleGather:
         shard, local = self.locate(ids)
         touched, src = np.unique(shard, return_inverse=True)
         src = src.reshape(-1)
+        if self.malformed == 'reference':
+            return self._gather_reference(shard, local, touched, src)
         decoded = []
         for j, s in enumerate(touched):
             reader = self.shards[int(s)]
@@ -146,6 +160,83 @@ class DeviceSampleGather:
                     reader._check_row(entry, int(idx))
             decoded.append(entry.decoded)
         return gather_sources(decoded, src, local)
+
+    def _gather_reference(self, shard: np.ndarray, local: np.ndarray, touched: np.ndarray,
+                          src: np.ndarray) -> DecodedBatch:
+        """:meth:`gather` under ``malformed='reference'``: a batch of what the reference's
+        ``__iter__`` yields for these samples (``dataset.py:1511``: whatever ``get_item`` returns,
+        clipped values included), raising only where the reference raises.
+
+        Rows of a touched shard whose decode reported an empty or out-of-range sample come from
+        the decoded shard where they pass its checks (``MDSReader._row_fits``); the others, and
+        every row of a shard whose header does not match its file (the reference never checks the
+        header), are *patch rows*: each is read as the reference reads it (``get_sample_data``:
+        short at the end of the file, wrapping where ``end < begin``), all of the batch's are
+        decoded in one ``MDSReader.decode_samples`` call, and the result is one more source of the
+        multi-source gather, so the gather kernels see nothing new.
+
+        The reference raises for a patch row whose read was empty, whose decode status is
+        ``SHORT_HEAD`` or ``SHORT_FIXED`` (numpy raises), or which is ``CLIPPED`` with a ``str``
+        slice that is not well-formed UTF-8 as clipped; the batch raises the exception of the
+        first such row in batch order, obtained from ``get_item`` (the reference's type). A row
+        whose columns are all whole keeps the device convention: a flag, no exception."""
+        sources: list[DecodedBatch] = []
+        where = np.full(len(touched), -1, np.int64)  # touched shard -> its place in `sources`
+        patch = np.zeros(src.size, bool)
+        for j, s in enumerate(touched):
+            reader = self.shards[int(s)]
+            os.stat(reader._filename())  # FileNotFoundError once evicted (the reference's open())
+            entry = reader._decode_entry()
+            mine = src == j
+            code = entry.status.code
+            if code == _native.MDSX_E_HEADER:
+                patch |= mine
+            elif code in (_native.MDSX_E_EMPTY, _native.MDSX_E_BOUNDS):
+                refused = [int(i) for i in np.unique(local[mine]) if not reader._row_fits(int(i))]
+                patch |= mine & np.isin(local, refused)
+            elif code != 0:
+                raise _status_error(entry.status, reader.plan)
+            if (mine & ~patch).any():
+                where[j] = len(sources)
+                sources.append(entry.decoded)
+        src, rows = where[src], local.copy()
+        pos = np.flatnonzero(patch)  # (batch order)
+        if pos.size:
+            datas: list[bytes] = []
+            index: dict[tuple[int, int], int] = {}
+            empty = []
+            prow = np.empty(pos.size, np.int64)
+            for t, k in enumerate(pos):
+                key = (int(shard[k]), int(local[k]))
+                r = index.get(key)
+                if r is None:
+                    r = index[key] = len(datas)
+                    try:
+                        datas.append(self.shards[key[0]].get_sample_data(key[1]))
+                    except IndexError:  # an empty read: this sample's outcome
+                        datas.append(b'')
+                        empty.append(r)
+                prow[t] = r
+            out, status = self.shards[int(shard[pos[0]])].decode_samples(datas)
+            raises = status >= _native.SAMPLE_SHORT_HEAD
+            raises[empty] = True
+            clipped = status == _native.SAMPLE_CLIPPED
+            if clipped.any():
+                for col in out.columns.values():
+                    if isinstance(col, RaggedColumn) and col.flags is not None:
+                        raises |= clipped & (col.flags.cpu().numpy() != 0)
+            for t, k in enumerate(pos):
+                if raises[prow[t]]:
+                    reader, idx = self.shards[int(shard[k])], int(local[k])
+                    reader.get_item(idx)  # raises what the reference raises for this sample
+                    raise RuntimeError(
+                        f'MDS sample {idx} of {reader.raw_data.basename}: the batched sample '
+                        f'decode reports status {int(status[prow[t]])} (the reference raises), '
+                        'but the per-sample reader returned a value')
+            src[pos] = len(sources)
+            rows[pos] = prow
+            sources.append(out)
+        return gather_sources(sources, src, rows)
 
     def iter_batches(self, sample_ids: Union[Sequence[int], np.ndarray, torch.Tensor],
                      batch_size: int) -> Iterator[DecodedBatch]:

@@ -163,7 +163,8 @@ def _gather_batch(dataset: Any, gather: Any, ids: list, retry: int) -> DecodedBa
 
 def device_iter(dataset: Any, batch_size: int, *, num_workers: int = 0, retry: int = 7,
                 gather: Optional[Any] = None,
-                exchange: Union[bool, Any, None] = None) -> Iterator[DecodedBatch]:
+                exchange: Union[bool, Any, None] = None,
+                malformed: str = 'strict') -> Iterator[DecodedBatch]:
     """``StreamingDataset.__iter__`` (``dataset.py:1475-1513``) yielding DEVICE batches, in the
     order ``DataLoader(dataset, batch_size, num_workers=num_workers)`` yields them on this rank.
 
@@ -192,7 +193,9 @@ def device_iter(dataset: Any, batch_size: int, *, num_workers: int = 0, retry: i
     The dataset's shards must be device readers (``stream_name='mdsx'``,
     :func:`register_device_stream`). ``gather``: what turns ids into a batch (default: a
     ``DeviceSampleGather`` over ``dataset.shards``); an object with ``gather(ids)``,
-    ``locate(ids)`` and ``shards``.
+    ``locate(ids)`` and ``shards``. ``malformed`` (``'strict'`` or ``'reference'``, used only
+    when the default gather is built): whether a batch reading a sample that breaks the MDS layout
+    raises, or yields the clipped values the reference yields.
 
     ``exchange``: ``True`` (the default process group) or a process group -- each shard is
     decoded by one rank of the group and every batch's rows are exchanged between the ranks
@@ -213,7 +216,7 @@ def device_iter(dataset: Any, batch_size: int, *, num_workers: int = 0, retry: i
             raise TypeError(f'device_iter: shard {bad[0]} is a {type(ds.shards[bad[0]]).__name__}, '
                             f'not a device reader (build the dataset with stream_name=\'mdsx\', '
                             f'streaming_amd.plugin.register_device_stream)')
-        gather = DeviceSampleGather(ds.shards)
+        gather = DeviceSampleGather(ds.shards, malformed=malformed)
     if exchange:
         from streaming_amd.exchange import OwnedShardGather
         gather = OwnedShardGather(gather, batch_size, group=None if exchange is True else exchange,

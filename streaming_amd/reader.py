@@ -28,7 +28,7 @@ import sys
 import threading
 from copy import deepcopy
 from dataclasses import dataclass
-from typing import Any, Iterator, Optional, Union
+from typing import Any, Iterator, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -42,7 +42,8 @@ from streaming_amd.encodings import (host_object_decode, is_mds_encoding_safe,
                                      ndarray_dyn_decode, parse_encoding)
 from streaming_amd.writer import bytes_to_int
 
-__all__ = ['FileInfo', 'Reader', 'JointReader', 'MDSReader', 'get_plan', 'reader_from_json']
+__all__ = ['FileInfo', 'Reader', 'JointReader', 'MDSReader', 'get_plan', 'reader_from_json',
+           'pack_samples', 'packed_bytes']
 
 _plan_lock = threading.Lock()
 _plans: dict[tuple, Plan] = {}
@@ -58,6 +59,47 @@ def get_plan(column_names, column_encodings, column_sizes) -> Plan:
             plan = Plan(column_names, column_encodings, column_sizes)
             _plans[key] = plan
     return plan
+
+
+def packed_bytes(lengths: Sequence[int]) -> int:
+    """Bytes of the buffer :func:`pack_samples` fills for samples of these lengths."""
+    m = len(lengths)
+    table = (12 * m + 63) // 64 * 64
+    return table + 2 * _native.SAMPLE_SLACK + int(sum(int(n) for n in lengths))
+
+
+def pack_samples(datas: Sequence[bytes], out: Optional[np.ndarray] = None
+                 ) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The input of ``mdsx_decode_samples_*`` for the samples ``datas``, in ONE host buffer (one
+    H2D): the table -- ``uint64[m]`` offsets, then ``uint32[m]`` lengths, padded to 64 bytes --
+    then 64 zero bytes, the samples' bytes back to back (every source alignment occurs; an empty
+    sample takes no bytes), and 64 zero bytes: the slack the kernels' aligned loads may read
+    before the first sample and after the last.
+
+    Returns ``(buffer, offsets, lengths)``; ``offsets`` (each sample's first byte in ``buffer``)
+    and ``lengths`` are views of ``buffer``'s table. ``out``: a uint8 array of
+    ``packed_bytes([len(d) for d in datas])`` bytes to fill (a pinned staging buffer)."""
+    m = len(datas)
+    lens = [len(d) for d in datas]
+    if any(n >= 1 << 32 for n in lens):
+        raise ValueError('pack_samples: a sample of 4 GiB or more')
+    total = packed_bytes(lens)
+    if out is None:
+        out = np.empty(total, np.uint8)
+    if out.dtype != np.uint8 or out.ndim != 1 or out.size != total:
+        raise ValueError(f'pack_samples: `out` must be a uint8 array of {total} bytes')
+    table = (12 * m + 63) // 64 * 64
+    first = table + _native.SAMPLE_SLACK
+    offsets = out[:8 * m].view(np.uint64)
+    lengths = out[8 * m:12 * m].view(np.uint32)
+    lengths[:] = lens
+    offsets[:] = first + np.cumsum(lengths, dtype=np.uint64) - lengths
+    out[12 * m:first] = 0
+    end = first + int(sum(lens))
+    if end > first:
+        out[first:end] = np.frombuffer(b''.join(datas), np.uint8)
+    out[end:] = 0
+    return out, offsets, lengths
 
 
 @dataclass
@@ -558,6 +600,79 @@ class MDSReader(JointReader):
             else:  # ragged, or a fixed column clipped short: its decoder sees the short slice
                 sample[col.name] = self._value(enc, info, raw.tobytes(), fixed=False)
         return sample
+
+
+    def decode_samples(self, datas: Sequence[bytes]) -> tuple[DecodedBatch, np.ndarray]:
+        """Decode many samples' bytes on the device, each sliced as :meth:`decode_sample` slices
+        one (mds/reader.py:103-126), into a device batch of ``len(datas)`` rows with the columns
+        the whole-shard decode gives (fixed tensors; :class:`RaggedColumn`, with ``flags`` for
+        ``str``): ``mdsx_decode_samples_sizes`` + ``mdsx_decode_samples_copy``, one H2D of the
+        packed samples (:func:`pack_samples`) and one host sync (the ragged totals, read with the
+        status).
+
+        Returns the batch and the host ``int32[m]`` status of each row (``_native.SAMPLE_*``):
+        ``OK``; ``CLIPPED`` -- a ragged slice shorter than its head, handed out as the reference
+        hands it out (a ``str`` row's flag then says whether ``bytes.decode`` raises on the
+        clipped slice); ``SHORT_HEAD`` / ``SHORT_FIXED`` -- the reference's numpy decode raises
+        (the row's fixed columns are zero, its ragged slices as clipped)."""
+        _native.check_fork()
+        _native.require_gpu()
+        plan = self.plan
+        m = len(datas)
+        if m == 0:
+            raise ValueError('decode_samples: no samples')
+        dev = torch.device(self.device or 'cuda')
+        if dev.type != 'cuda':  # host addresses must never reach the kernels
+            raise ValueError(f'decode_samples: device {dev} is not a GPU')
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        lib = _native.lib()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            total = packed_bytes([len(d) for d in datas])
+            host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            pack_samples(datas, out=host.numpy())
+            buf = host.to(dev, non_blocking=True)  # (`host` outlives the copy: the sync below)
+            base = buf.data_ptr()
+            table = (base, total, base, base + 8 * m, m)
+            nvar = plan.num_var
+            lens = torch.zeros((max(nvar, 1), m + 1), dtype=torch.int64, device=dev)
+            status = torch.zeros((m, 2), dtype=torch.int32, device=dev)
+            _check(lib.mdsx_decode_samples_sizes(plan.handle, *table, lens.data_ptr(),
+                                                 status.data_ptr(), stream.cuda_stream),
+                   'mdsx_decode_samples_sizes')
+            offs = torch.cumsum(lens, 1)
+            # the one sync: the totals that size the value buffers, and the status
+            head = torch.cat([offs[:, -1], status.view(torch.int64).reshape(-1)]).cpu().numpy()
+            caps = head[:max(nvar, 1)]
+            st = head[max(nvar, 1):].view(np.int32).reshape(m, 2)[:, 0].copy()
+            if (st < 0).any():
+                raise RuntimeError(f'decode_samples: sample {int(np.argmax(st < 0))} lies outside '
+                                   'the packed buffer')
+            outs = (_native.ColumnOut * max(len(plan.columns), 1))()
+            cols: dict[str, Union[torch.Tensor, RaggedColumn]] = {}
+            vi = 0
+            for col in plan.columns:
+                o = outs[col.index]
+                if col.is_fixed:
+                    raw = torch.zeros((m, col.row_bytes), dtype=torch.uint8, device=dev)
+                    o.data, o.offsets, o.flags, o.capacity = raw.data_ptr(), None, None, 0
+                    dtype, shape = col.tensor_view()
+                    cols[col.name] = raw.view(dtype).reshape((m, ) + shape)
+                else:
+                    cap = int(caps[vi])
+                    vals = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+                    flags = torch.zeros(m, dtype=torch.uint8, device=dev) \
+                        if col.kind == _native.KIND_STR else None
+                    o.data = vals.data_ptr() if cap else None
+                    o.offsets = offs[vi].data_ptr()
+                    o.flags = flags.data_ptr() if flags is not None else None
+                    o.capacity = cap
+                    cols[col.name] = RaggedColumn(vals[:cap], offs[vi], flags)
+                    vi += 1
+            _check(lib.mdsx_decode_samples_copy(plan.handle, *table, outs, stream.cuda_stream),
+                   'mdsx_decode_samples_copy')
+        return DecodedBatch(cols, m, stream=stream), st
 
 
 def reader_from_json(dirname: str, split: Optional[str], obj: dict[str, Any],
