@@ -323,6 +323,52 @@ int mdsx_ndarray_meta(const uint8_t* values, const int64_t* offsets, uint64_t ro
 int mdsx_ndarray_shapes(const uint8_t* values, const int64_t* offsets, uint64_t rows,
                         int dtype_id, int32_t shape_cols, int64_t* out_shape, void* stream);
 
+/* ---- collate: dense and packed typed batches from ragged columns ------------------------------
+ * The step between a decoded ragged column (values + byte offsets) and a model: the rows' elements
+ * as dtype[rows, width] (pad) or back to back with element offsets (pack). A row is, by
+ * row_model, MDSX_ROWS_PLAIN: the bytes of a 'bytes' (any MDSX_KIND_BYTES) row read as elements of
+ * src_dtype, as numpy.frombuffer would; MDSX_ROWS_NDARRAY_STATIC: a row of 'ndarray:<dtype>',
+ * whose header is parsed as NDArray.decode parses it (encodings.py:270-305; the same parse as
+ * mdsx_ndarray_meta); MDSX_ROWS_NDARRAY_DYN: a row of 'ndarray', which carries its dtype id.
+ * src_dtype / dst_dtype are value dtype ids (encodings.py:131-143). A row's elements are its value
+ * bytes in memory (C) order. Per-row status: 0 good; 1 the reference's decode raises, or a plain
+ * row is not a whole number of elements; 2 (MDSX_ROWS_NDARRAY_DYN only) a well-formed row of
+ * another dtype than src_dtype. Rows with a non-zero status have no elements.
+ * dst_dtype == src_dtype is a bit copy; int8/uint8/int16/uint16 -> int32/int64 and
+ * int32/uint32 -> int64 sign- or zero-extend; any other pair is MDSX_E_ARG. Every argument is
+ * checked before any HIP call; rows == 0 launches nothing.
+ *
+ * mdsx_ragged_elems: the sizing pass, needed only for a size the caller does not know:
+ *   out_count int64[rows], out_status uint8[rows], and d_record int64[3] (zeroed by the caller)
+ *   = {largest count, sum of counts, rows with a non-zero status}.
+ * mdsx_ragged_pad: one launch, no earlier pass. dst[rows, width] of dst_dtype (aligned to its
+ *   item; width x item < 2^32); `side`: the end of the destination row the elements sit at;
+ *   `truncate`: MDSX_SIDE_RIGHT keeps the first `width` elements of a longer row, MDSX_SIDE_LEFT
+ *   the last; pad_bits: the pad element's bit pattern in its low bytes. out_len int64[rows] gets
+ *   the elements kept, out_status the status; a row with a non-zero status is all pad, length 0.
+ *   d_bad_count (device int64, zeroed by the caller, may be NULL) counts the non-zero statuses.
+ *   Every byte of dst is written exactly once and no byte outside it: pass uninitialised memory.
+ * mdsx_ragged_pack: d_count from mdsx_ragged_elems (same column and dtypes) is scanned into
+ *   out_offsets int64[rows + 1] (element offsets; with rows == 0 nothing is written) and each
+ *   row's values are copied to dst + out_offsets[i] x item, headers stripped. dst_capacity:
+ *   elements of dst (the record's sum). The workspace is mdsx_gather_workspace_bytes(rows). */
+#define MDSX_ROWS_PLAIN 0
+#define MDSX_ROWS_NDARRAY_STATIC 1
+#define MDSX_ROWS_NDARRAY_DYN 2
+#define MDSX_SIDE_RIGHT 0
+#define MDSX_SIDE_LEFT 1
+int mdsx_ragged_elems(const uint8_t* values, const int64_t* offsets, uint64_t rows, int row_model,
+                      int src_dtype, int64_t* out_count, uint8_t* out_status, int64_t* d_record,
+                      void* stream);
+int mdsx_ragged_pad(const uint8_t* values, const int64_t* offsets, uint64_t rows, int row_model,
+                    int src_dtype, int dst_dtype, void* dst, uint64_t width, int side,
+                    int truncate, uint64_t pad_bits, int64_t* out_len, uint8_t* out_status,
+                    int64_t* d_bad_count, void* stream);
+int mdsx_ragged_pack(const uint8_t* values, const int64_t* offsets, uint64_t rows, int row_model,
+                     int src_dtype, int dst_dtype, const int64_t* d_count, void* dst,
+                     uint64_t dst_capacity, int64_t* out_offsets, void* d_workspace,
+                     uint64_t workspace_bytes, void* stream);
+
 /* ---- shard encode (MDSWriter on the device) ----------------------------------------------------
  * The reverse of the decode: columns in the decoder's output layout -> MDS shard files,
  * byte-identical to the reference writer's. Replaces MDSWriter.encode_sample +

@@ -7,6 +7,8 @@ whole shards -- runs as hand-written gfx950 HIP kernels in ``libmdsx.so`` (C ABI
 """
 
 from streaming_amd.array import Array
+from streaming_amd.collate import (Pack, PackedColumn, Pad, PaddedColumn, pack_ragged,
+                                   pad_ragged)
 from streaming_amd.decoder import (BatchDecoder, DecodedBatch, DeviceBatch, Plan, RaggedColumn,
                                    decode_batch, stage_shards)
 from streaming_amd.local import LocalDataset, shard_assignment
@@ -18,6 +20,7 @@ __version__ = '0.1.0'
 
 __all__ = [
     'Array', 'BatchDecoder', 'DecodedBatch', 'DeviceBatch', 'FileInfo', 'JointReader',
-    'LocalDataset', 'MDSReader', 'MDSWriter', 'Plan', 'RaggedColumn', 'Reader', 'Spanner',
-    'decode_batch', 'reader_from_json', 'shard_assignment', 'stage_shards'
+    'LocalDataset', 'MDSReader', 'MDSWriter', 'Pack', 'PackedColumn', 'Pad', 'PaddedColumn', 'Plan',
+    'RaggedColumn', 'Reader', 'Spanner', 'decode_batch', 'pack_ragged', 'pad_ragged',
+    'reader_from_json', 'shard_assignment', 'stage_shards'
 ]

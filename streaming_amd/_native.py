@@ -80,6 +80,9 @@ EXPORTED_SYMBOLS = (
     'mdsx_gather_ragged_copy_multi',
     'mdsx_ndarray_meta',
     'mdsx_ndarray_shapes',
+    'mdsx_ragged_elems',
+    'mdsx_ragged_pad',
+    'mdsx_ragged_pack',
     'mdsx_plan_encode_tile_rows',
     'mdsx_encode_workspace_bytes',
     'mdsx_encode_sizes',
@@ -87,6 +90,13 @@ EXPORTED_SYMBOLS = (
     'mdsx_hash_workspace_bytes',
     'mdsx_hash_segments',
 )
+
+# mdsx_ragged_*: row models and sides (include/mdsx.h)
+ROWS_PLAIN = 0
+ROWS_NDARRAY_STATIC = 1
+ROWS_NDARRAY_DYN = 2
+SIDE_RIGHT = 0
+SIDE_LEFT = 1
 
 HASH_XXH32 = 1
 HASH_XXH64 = 2
@@ -206,6 +216,14 @@ def _declare(handle: ctypes.CDLL) -> None:
     handle.mdsx_ndarray_meta.argtypes = [vp, vp, c_u64, c_int, vp, vp, vp, vp, vp, vp, vp]
     handle.mdsx_ndarray_shapes.restype = c_int
     handle.mdsx_ndarray_shapes.argtypes = [vp, vp, c_u64, c_int, ctypes.c_int32, vp, vp]
+    handle.mdsx_ragged_elems.restype = c_int
+    handle.mdsx_ragged_elems.argtypes = [vp, vp, c_u64, c_int, c_int, vp, vp, vp, vp]
+    handle.mdsx_ragged_pad.restype = c_int
+    handle.mdsx_ragged_pad.argtypes = [vp, vp, c_u64, c_int, c_int, c_int, vp, c_u64, c_int, c_int,
+                                       c_u64, vp, vp, vp, vp]
+    handle.mdsx_ragged_pack.restype = c_int
+    handle.mdsx_ragged_pack.argtypes = [vp, vp, c_u64, c_int, c_int, c_int, vp, vp, c_u64, vp, vp,
+                                        c_u64, vp]
     handle.mdsx_plan_encode_tile_rows.restype = c_int
     handle.mdsx_plan_encode_tile_rows.argtypes = [vp]
     handle.mdsx_encode_workspace_bytes.restype = c_u64

@@ -16,11 +16,12 @@ ROOT = os.path.dirname(HERE)
 SOURCES = [
     os.path.join(HERE, 'csrc', name)
     for name in ('mdsx_kernels.hip', 'mdsx_stage.hip', 'mdsx_run.hip', 'mdsx_rows.hip', 'mdsx_swave.hip',
-                 'mdsx_sample.hip', 'mdsx_samples.hip', 'mdsx_encode.hip', 'mdsx_hash.hip', 'mdsx_plan.cpp')
+                 'mdsx_sample.hip', 'mdsx_samples.hip', 'mdsx_encode.hip', 'mdsx_hash.hip',
+                 'mdsx_collate.hip', 'mdsx_plan.cpp')
 ]
 HEADERS = [os.path.join(HERE, 'csrc', name)
            for name in ('mdsx_internal.h', 'mdsx_device.h', 'mdsx_decode.h', 'mdsx_ring.h',
-                        'mdsx_run_body.h')]
+                        'mdsx_run_body.h', 'mdsx_ndarray.h')]
 OUTPUT = os.path.join(HERE, 'lib', 'libmdsx.so')
 ARCH = os.environ.get('MDSX_OFFLOAD_ARCH', 'gfx950')
 
@@ -88,6 +89,8 @@ ISA_CHECKED = {
     'mdsx_swave.hip': ('swave_decode_kernel',),
     # the batched sample decode: a wave picks its sample, then copies with readlane / DPP
     'mdsx_samples.hip': ('samples_sizes_kernel', 'samples_copy_kernel'),
+    # collate: wave_copy / group_copy over rows a wave parsed itself (every instantiation)
+    'mdsx_collate.hip': ('ragged_pad_kernel', 'ragged_pack_kernel'),
 }
 
 
@@ -110,7 +113,11 @@ def _check_cross_lane_reads(obj: str, want: tuple = ('rows_decode_kernel',)) -> 
 
 # Kernels that must not spill at all: a VGPR reloaded from scratch under a partial exec mask holds
 # stale bits in its inactive lanes, which a later cross-lane read with every lane active returns.
-NO_SCRATCH = {'mdsx_swave.hip': ('swave_decode_kernel',)}
+NO_SCRATCH = {
+    'mdsx_swave.hip': ('swave_decode_kernel',),
+    # the collate copies read across lanes after per-row branches, the same hazard
+    'mdsx_collate.hip': ('ragged_pad_kernel', 'ragged_pack_kernel'),
+}
 
 
 def _check_no_scratch(obj: str, want: tuple) -> None:

@@ -40,6 +40,7 @@
 #include "mdsx_decode.h"
 #include "mdsx_device.h"
 #include "mdsx_internal.h"
+#include "mdsx_ndarray.h"
 
 namespace mdsx_kernels {
 
@@ -1314,18 +1315,8 @@ __global__ __launch_bounds__(kBlock) void gather_copy_kernel(
 // ---------------------------------------------------------------------------------------------
 // Dynamic ndarray columns ('ndarray', 'ndarray:<dtype>'): per-row header parse over the decoded
 // ragged values -- NDArray.decode (encodings.py:270-305): [dtype id: u8 if dynamic]
-// [ndim << 2 | shape dtype: u8][shape: ndim x u8/u16/u32/u64][values]. One row per lane.
-__device__ __forceinline__ bool value_dtype_ok(uint32_t id) {
-  return id == 8 || id == 9 || id == 16 || id == 17 || id == 18 || id == 32 || id == 33 ||
-         id == 34 || id == 64 || id == 65 || id == 66;
-}
-
-__device__ __forceinline__ uint64_t read_uint(const uint8_t* p, int nbytes) {
-  uint64_t v = 0;
-  for (int b = 0; b < nbytes; ++b) v |= uint64_t(p[b]) << (8 * b);
-  return v;
-}
-
+// [ndim << 2 | shape dtype: u8][shape: ndim x u8/u16/u32/u64][values]. One row per lane; the parse
+// itself is ndarray_parse_row (mdsx_ndarray.h), shared with the collate kernels.
 template <bool kShapes>
 __global__ __launch_bounds__(kBlock) void ndarray_meta_kernel(
     const uint8_t* values, const int64_t* offsets, uint64_t rows, int dtype_id, uint8_t* out_dtype,
@@ -1335,51 +1326,11 @@ __global__ __launch_bounds__(kBlock) void ndarray_meta_kernel(
   if (r >= rows) return;
   const int64_t b = offsets[r], e = offsets[r + 1];
   const uint8_t* p = values + b;
-  const int64_t len = e - b;
-  int64_t pos = 0;
-  bool bad = false;
-  uint32_t id = uint32_t(dtype_id);
-  if (id == 0) {
-    if (len < 1) bad = true;
-    else id = p[pos++];
-    if (!bad && !value_dtype_ok(id)) bad = true;
-  }
-  uint32_t ndim = 0, code = 0;
-  if (!bad) {
-    if (pos + 1 > len) bad = true;
-    else {
-      const uint32_t byte = p[pos++];
-      ndim = byte >> 2;
-      code = byte & 3;
-    }
-  }
-  // shape = frombuffer(data[index:index + ndim * sbytes], shape dtype): a truncated header
-  // yields fewer dims (or raises when the tail is not whole dims); the values then start past
-  // the end and are empty.
-  const int sbytes = 1 << code;
-  const int64_t want = int64_t(ndim) * sbytes;
-  if (!bad && want > len - pos) {
-    if ((len - pos) % sbytes) bad = true;
-    else ndim = uint32_t((len - pos) / sbytes);
-  }
-  // numpy's size rule (PyArray_NewFromDescr): zero dims make the array empty, the product of
-  // the non-zero dims times the item size must fit in intp; dims above intp max raise.
-  const int64_t item = int64_t(id >> 3);
-  int64_t prod = item;
-  bool zero = false;
-  if (!bad) {
-    for (uint32_t k = 0; k < ndim; ++k) {
-      const uint64_t dim = read_uint(p + pos + k * sbytes, sbytes);
-      if (kShapes && int32_t(k) < shape_cols) out_shape[r * shape_cols + k] = int64_t(dim);
-      if (dim > uint64_t(INT64_MAX)) { bad = true; break; }
-      if (dim == 0) { zero = true; continue; }
-      if (__builtin_mul_overflow(prod, int64_t(dim), &prod)) { bad = true; break; }
-    }
-    pos = pos + want < len ? pos + want : len;
-  }
-  const int64_t numel = (bad || zero) ? 0 : prod / item;
-  // frombuffer(data[index:], dtype).reshape(shape): the value bytes must be exactly numel items
-  if (!bad && (len - pos) != numel * item) bad = true;
+  const NdRow h = ndarray_parse_row<kShapes>(p, e - b, dtype_id, shape_cols,
+                                             kShapes ? out_shape + r * shape_cols : nullptr);
+  const bool bad = h.bad;
+  const uint32_t id = h.id, ndim = h.ndim;
+  const int64_t pos = h.pos, numel = h.numel;
   if (kShapes) {
     for (int32_t k = int32_t(ndim); k < shape_cols; ++k) out_shape[r * shape_cols + k] = 1;
     return;
@@ -1387,7 +1338,7 @@ __global__ __launch_bounds__(kBlock) void ndarray_meta_kernel(
   out_dtype[r] = uint8_t(bad ? 0 : id);
   out_ndim[r] = uint8_t(bad ? 0 : ndim);
   out_data_offset[r] = b + pos;
-  out_numel[r] = bad ? 0 : numel;
+  out_numel[r] = numel;
   out_bad[r] = bad ? 1 : 0;
   if (!bad && max_ndim) atomicMax(max_ndim, int32_t(ndim));
 }

@@ -378,9 +378,29 @@ class DecodedBatch:
         for col in self.columns.values():
             if isinstance(col, RaggedColumn):
                 out += [t for t in (col.values, col.offsets, col.flags) if t is not None]
-            else:
+            elif isinstance(col, torch.Tensor):
                 out.append(col)
+            else:  # a collated column (streaming_amd.collate)
+                out += col.tensors()
         return out
+
+    def collate(self, spec: dict, plan: 'Plan') -> 'DecodedBatch':
+        """This batch with the ragged columns named in ``spec`` (name ->
+        :class:`streaming_amd.collate.Pad` / :class:`~streaming_amd.collate.Pack`) replaced by
+        their :class:`~streaming_amd.collate.PaddedColumn` / ``PackedColumn``
+        (``mdsx_ragged_pad`` / ``mdsx_ragged_pack``; the encodings come from ``plan``). The other
+        columns are shared with this batch, not copied. Host syncs: those of
+        :func:`~streaming_amd.collate.pad_ragged` / ``pack_ragged``, per named column."""
+        from streaming_amd.collate import collate_columns
+        encodings = {c.name: c.encoding for c in plan.columns}
+        stream = self.stream
+        named = [self.columns[n] for n in spec if isinstance(self.columns.get(n), RaggedColumn)]
+        if named and named[0].values.device.type == 'cuda':
+            dev = named[0].values.device
+            _on_current_stream([self], dev)  # the kernels read this batch on the current stream
+            stream = torch.cuda.current_stream(dev)
+        return DecodedBatch(collate_columns(self.columns, spec, encodings), self.rows,
+                            list(self.row0), stream, self.sample_ids)
 
     def __getitem__(self, name: str) -> Union[torch.Tensor, RaggedColumn]:
         return self.columns[name]

@@ -77,7 +77,8 @@ class LocalDataset(Array, Dataset):
         return self.shards[shard_id][index_in_shard]
 
     def iter_batches(self, sample_ids: Union[Sequence[int], np.ndarray, torch.Tensor],
-                     batch_size: int, malformed: str = 'strict') -> Iterator[DecodedBatch]:
+                     batch_size: int, malformed: str = 'strict',
+                     collate: Optional[dict] = None) -> Iterator[DecodedBatch]:
         """Device batches of ``batch_size`` samples in the order of ``sample_ids`` (global ids,
         ``-1`` padding skipped as the reference's ``_each_sample_id`` does,
         ``dataset.py:1430-1473``; e.g. one worker's slice of ``generate_work``'s ids,
@@ -86,9 +87,15 @@ class LocalDataset(Array, Dataset):
         (:class:`streaming_amd.order.DeviceSampleGather`). ``malformed``: ``'strict'`` -- a
         batch reading a sample that breaks the MDS layout raises -- or ``'reference'`` -- it
         yields the clipped values the reference's loader yields and raises only where the
-        reference raises."""
-        return DeviceSampleGather(self.shards, malformed=malformed).iter_batches(sample_ids,
-                                                                                batch_size)
+        reference raises. ``collate``: column name ->
+        :class:`streaming_amd.collate.Pad` / ``Pack``, applied to each batch
+        (:meth:`DecodedBatch.collate`); None: the batches as gathered."""
+        batches = DeviceSampleGather(self.shards, malformed=malformed).iter_batches(sample_ids,
+                                                                                   batch_size)
+        if collate is None:
+            return batches
+        plan = self.shards[0].plan
+        return (batch.collate(collate, plan) for batch in batches)
 
     @property
     def sample_gather(self) -> DeviceSampleGather:

@@ -164,7 +164,8 @@ def _gather_batch(dataset: Any, gather: Any, ids: list, retry: int) -> DecodedBa
 def device_iter(dataset: Any, batch_size: int, *, num_workers: int = 0, retry: int = 7,
                 gather: Optional[Any] = None,
                 exchange: Union[bool, Any, None] = None,
-                malformed: str = 'strict') -> Iterator[DecodedBatch]:
+                malformed: str = 'strict',
+                collate: Optional[dict] = None) -> Iterator[DecodedBatch]:
     """``StreamingDataset.__iter__`` (``dataset.py:1475-1513``) yielding DEVICE batches, in the
     order ``DataLoader(dataset, batch_size, num_workers=num_workers)`` yields them on this rank.
 
@@ -203,6 +204,11 @@ def device_iter(dataset: Any, batch_size: int, *, num_workers: int = 0, retry: i
     decoding every shard its batches touch. The batches are the same. Every rank of the group
     runs ``device_iter`` over the same epoch; a rank out of batches (or stopped early) keeps
     serving the others' requests until every rank is out.
+
+    ``collate``: column name -> :class:`streaming_amd.collate.Pad` / ``Pack``; each batch's named
+    ragged columns are padded / packed on the device after the gather
+    (:meth:`DecodedBatch.collate`, with the encodings of ``gather.shards[0].plan``). None: the
+    batches as gathered.
     """
     if batch_size <= 0:
         raise ValueError('batch_size must be positive')
@@ -223,7 +229,11 @@ def device_iter(dataset: Any, batch_size: int, *, num_workers: int = 0, retry: i
                                   prepare=getattr(ds, 'prepare_shard', None))
     drain = getattr(gather, 'drain', None)
     try:
-        yield from _device_iter(ds, mod, gather, batch_size, workers, retry)
+        if collate is None:
+            yield from _device_iter(ds, mod, gather, batch_size, workers, retry)
+        else:
+            for batch in _device_iter(ds, mod, gather, batch_size, workers, retry):
+                yield batch.collate(collate, gather.shards[0].plan)
     finally:
         if drain is not None:  # (every rank of the exchange group takes part until all are out)
             drain()
